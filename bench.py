@@ -8,7 +8,9 @@ Either form works for N > 1: without a launcher's environment (no WORLD_SIZE) `-
 process per GPU under torch.distributed.run on 127.0.0.1, like the reference's drivers launch their own workers
 (experiments/cholesky_experiment.py:170) -- and a line is only ever printed when exactly N ranks joined: `n_gpus` is
 the size of the job that ran, `config.ranks_joined` / `config.devices` / `config.rccl_nranks` are the evidence.
-`--dry-run` stops after the rendezvous and prints who joined (no GPU work).
+`--dry-run` stops after the rendezvous and prints who joined (no GPU work).  `--dump-outputs DIR` (one GPU) writes what the
+last timed step returned as DIR/<name>.npy -- L, R / V / T or C; a seeded sample when larger than 64 MB in all -- so
+two builds can be compared output for output (the inputs are seeded: the same on every run with the same arguments).
 
 metric : achieved fp64 TFLOP/s of an N x N tiled Cholesky (4096^2 tiles) = (N^3 / 3) / wall, whole job.
 step   : one complete factorisation (alg_wrappers.cholesky -> LambdaPACK DAG -> HIP-stream executor)
@@ -465,6 +467,44 @@ def step_stats(step_ms, mean_ms, what="ms_per_step"):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this much in all, .npy headers included
+DUMP_HEADER = 4096          # room left for each file's .npy header
+DUMP_TILES = 16             # tiles sampled per output when it does not fit whole
+DUMP_SEED = 0
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: write what the last timed step returned -- `outputs` is [(name, BigMatrix)] -- as path/<name>.npy,
+    float32 where the stored tiles are fp32 and float64 otherwise.  An output's stored tiles are taken in sorted index
+    order -- those beyond the nominal grid included: TSQR keeps its final R one block row past the end, as the reference
+    does; if they do not all fit its share of DUMP_BYTES, a seeded choice of DUMP_TILES tiles and of elements inside each
+    tile is written instead (the same positions on every run with the same arguments).  Returns what was written."""
+    os.makedirs(path, exist_ok=True)
+    outputs = [(name, M, sorted(tuple(lo // s for (lo, _), s in zip(blk, M.shard_sizes)) for blk in M.blocks_exist))
+               for name, M in outputs]
+    outputs = [o for o in outputs if o[2]]
+    written = {}
+    for name, M, tiles in outputs:
+        dtype = np.float32 if np.dtype(M._raw(tiles[0])[0].dtype) == np.float32 else np.float64
+        cap = (DUMP_BYTES // len(outputs) - DUMP_HEADER) // np.dtype(dtype).itemsize
+        total = sum(int(np.prod(M._raw(t)[0].shape)) for t in tiles)
+        rng = np.random.default_rng(DUMP_SEED)
+        whole = total <= cap
+        if not whole:
+            tiles = [tiles[i] for i in sorted(rng.choice(len(tiles), min(len(tiles), DUMP_TILES), replace=False))]
+        parts = []
+        for t in tiles:
+            block = np.asarray(M.get_block(*t), dtype=dtype).ravel()
+            if not whole and block.size > cap // len(tiles):
+                block = block[np.sort(rng.choice(block.size, cap // len(tiles), replace=False))]
+            parts.append(block)
+        values = np.concatenate(parts)
+        np.save(os.path.join(path, name + ".npy"), values)
+        written[name] = {"matrix": M.key, "shape": list(M.shape), "dtype": np.dtype(dtype).name, "elements": int(values.size),
+                         "of": total, "tiles": [list(map(int, t)) for t in tiles], "sample_seed": None if whole else DUMP_SEED}
+    return written
+
+
 def cholesky_residual(be, X, O, nb, full=False):
     """|| A - L L^T ||_F / || A ||_F on the device: all tiles (full=True) or the tile (1, 1).  A PROPERTY check computed with
     this build's own GEMM (be.gemm) -- not an independent product: that GEMM is checked against the oracle at 4096^2 in
@@ -588,7 +628,14 @@ def main():
     ap.add_argument("--no-north-star", action="store_true", help="skip the 65536^2 single-GPU run of the N = 1 line")
     ap.add_argument("--no-anchor", action="store_true", help="N > 1: skip rank 0's one-GPU run of the same problem (config.one_gpu_anchor)")
     ap.add_argument("--dry-run", action="store_true", help="start / join the ranks, print who joined as one JSON line, do no GPU work")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (at most 64 MB in all; "
+                         "a seeded sample of larger outputs); one GPU only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs: one GPU only (with several ranks each one holds only its own tiles)")
     # dmabuf IPC between the ranks' processes (what RCCL needs on this driver stack); read by the HSA runtime when it starts, so it
     # has to be in the environment before the first HIP call of this process -- a launcher normally exports it, this is the net
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -665,6 +712,8 @@ def main():
         # inside the timed region only the roofline kernel is bracketed with events (an event record costs ~4 us of
         # stream time); the other kinds are timed in two extra steps after it, for `kernel_ms`
         elapsed, meta = run.timed(lambda: alg_wrappers.cholesky(X), args.steps, args.warmup, timers=("syrk",))
+        if args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, zip(["L"], meta["outputs"]))
         run_step_ms = run.step_ms
         flops = n ** 3 / 3.0
         value = args.steps * flops / elapsed / 1e12
@@ -764,6 +813,8 @@ def main():
                 X.put_tile(be.fill_random((b, b), 7, j * b, 0), j, 0)
         be.synchronize()
         elapsed, meta = run.timed(lambda: alg_wrappers.tsqr(X), args.steps, args.warmup, timers=("geqrt_batched", "tpqrt_batched"))
+        if args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, zip(["R", "V", "T"], meta["outputs"]))
         qr_times = be.collect_kernel_times() if comm is None else {}
         run_step_ms = run.step_ms
         flops = 2.0 * m * b * b - 2.0 * b ** 3 / 3
@@ -820,6 +871,8 @@ def main():
                     B.put_tile(be.convert(be.fill_random((b, b), 12, i * b, j * b), np.float32), i, j)
         be.synchronize()
         elapsed, meta = run.timed(lambda: alg_wrappers.gemm(A, B), args.steps, args.warmup, timers=("gemm",))
+        if args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, zip(["C"], meta["outputs"]))
         gemm_iv = be.collect_kernel_times(intervals=True).get("gemm", []) if comm is None else []
         gemm_times = [(e - s0) / max(1, c) for s0, e, c in gemm_iv]      # per product: a batched launch of c products / c
         gemm_products = sum(max(1, c) for _, _, c in gemm_iv)
@@ -876,6 +929,8 @@ def main():
             line["config"]["fused_pct_fp32_mfma_peak"] = round(100 * fused / 157.3, 2)
             line["config"]["fused_mode"] = "executor.fuse_gemm_reduction: fp32 accumulation in place, result converted to fp64 once"
     line.update(step_stats(run_step_ms, line["ms_per_step"]))
+    if args.dump_outputs:
+        line["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
     if comm is not None:
         line["config"]["transport"] = comm.backend
         if calib is not None:

@@ -301,8 +301,11 @@ class Comm(object):
 
     # ---- control-plane collectives (host side, tiny) ----
     def barrier(self):
+        # an all-reduce of one host value, not torch.distributed.barrier(): that one first asks torch for the machine's
+        # accelerator, which opens the GPU in every rank -- ranks of a host-only job (the oracle backend) included
         if self.world > 1:
-            self.dist.barrier()
+            import torch
+            self.dist.all_reduce(torch.zeros(1))
 
     def max_over_ranks(self, value):
         if self.world == 1:

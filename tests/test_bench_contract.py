@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,6 +73,65 @@ def test_bench_other_configs(workload, extra):
     assert "MKL" in cpu["blas"]
     if workload == "tsqr":
         assert roof["mfma_bound_ms_per_batch_of_32"] > 0 and roof["bound"] == "mfma" and line["config"]["r_only_run"]["roofline"]["achieved"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload,extra,names", [("chol", ["--tiles", "4"], ["L"]), ("tsqr", ["--leaves", "8"], ["R", "V", "T"]),
+                                                  ("gemm32", ["--tiles", "2"], ["C"])])
+def test_bench_dump_outputs(workload, extra, names, tmp_path):
+    """--dump-outputs DIR: what the last timed step returned, as DIR/<name>.npy (float32 / float64, at most 64 MB in all).
+    The inputs are seeded, so a second run with the same arguments writes the same numbers."""
+    runs = []
+    for k in range(2 if workload == "chol" else 1):
+        d = tmp_path / str(k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--tile", "512",
+               "--workload", workload, "--no-cpu-baseline", "--dump-outputs", str(d)] + extra
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert len(line["step_ms"]) == 2
+        info = line["outputs_dumped"]["files"]
+        assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in names) and sorted(info) == sorted(names)
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 * 10 ** 6
+        arrays = {n: np.load(str(d / (n + ".npy"))) for n in names}
+        for n, a in arrays.items():
+            assert a.dtype in (np.float32, np.float64) and a.size == info[n]["elements"] > 0 and np.isfinite(a).all()
+        runs.append(arrays)
+    if workload == "chol":
+        # small enough to be written whole: the lower tiles of L in index order, each a 512 x 512 tile
+        assert info["L"]["elements"] == info["L"]["of"] and info["L"]["sample_seed"] is None
+        tiles = runs[0]["L"].reshape(-1, 512, 512)
+        for (i, j), t in zip(info["L"]["tiles"], tiles):
+            assert i >= j
+            if i == j:
+                assert (np.triu(t, 1) == 0).all() and (np.diag(t) > 0).all()
+        np.testing.assert_allclose(runs[1]["L"], runs[0]["L"], rtol=1e-12, atol=0)
+
+
+def test_dump_outputs_writes_a_seeded_sample(tmp_path, host_store, monkeypatch):
+    """bench.dump_outputs on host-resident matrices: an output over its share of the budget becomes a seeded sample of its
+    tiles' elements (the same on every call), one that fits is written whole, an fp32 one stays fp32, an empty one is skipped."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from numpywren_amd.matrix import BigMatrix
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    A = np.random.default_rng(1).standard_normal((1024, 512))
+    M = BigMatrix("dump_big", shape=A.shape, shard_sizes=(256, 256))
+    for i in range(4):
+        for j in range(2):
+            M.put_block(A[i * 256:(i + 1) * 256, j * 256:(j + 1) * 256], i, j)
+    S = BigMatrix("dump_small", shape=(64, 64), shard_sizes=(32, 32), dtype=np.float32)
+    S.put_block(np.full((32, 32), 0.5, np.float32), 0, 1)
+    E = BigMatrix("dump_empty", shape=(8, 8), shard_sizes=(4, 4))
+    info = bench.dump_outputs(str(tmp_path / "a"), [("M", M), ("S", S), ("E", E)])
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["M.npy", "S.npy"] and sorted(info) == ["M", "S"]
+    m, s = np.load(str(tmp_path / "a" / "M.npy")), np.load(str(tmp_path / "a" / "S.npy"))
+    assert m.dtype == np.float64 and m.size == info["M"]["elements"] == ((1 << 20) // 2 - 4096) // 8 < info["M"]["of"] == A.size
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 1 << 20
+    assert np.isin(m, A).all() and len(np.unique(m)) == m.size and info["M"]["sample_seed"] is not None
+    assert s.dtype == np.float32 and (s == 0.5).all() and s.size == info["S"]["of"] == 1024 and info["S"]["tiles"] == [[0, 1]]
+    bench.dump_outputs(str(tmp_path / "b"), [("M", M), ("S", S)])
+    assert (np.load(str(tmp_path / "b" / "M.npy")) == m).all()
 
 
 def test_predicted_scaling_table_is_the_one_bench_quotes():
